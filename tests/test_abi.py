@@ -248,21 +248,21 @@ def test_go_shim_builds_with_the_reference_go_version_and_adds_only_new_names():
     assert "${SRCDIR}" not in raw
 
 
+def _ref_go():
+    """What the tests need of the reference's Go tree, as data
+    (tests/golden/ref_go.json, written by tests/golden/make_ref_go.py): the
+    top-level names of its packages, and where each hunk of the patch
+    applies with the digest of the lines it replaces."""
+    import json
+
+    with open(os.path.join(ROOT, "tests", "golden", "ref_go.json")) as f:
+        return json.load(f)
+
+
 def test_go_shim_names_do_not_collide_with_the_reference_package():
-    """Where the reference tree is present (this container), every top-level
-    identifier of its package header, in any file, differs from the shim's."""
-    hdr = "/root/reference/tcpip/header"
-    if not os.path.isdir(hdr):
-        pytest.skip("reference tree absent")
-    ref = set()
-    for fn in os.listdir(hdr):
-        if fn.endswith(".go") and not fn.endswith("_test.go"):
-            code = _go_code(open(os.path.join(hdr, fn)).read())
-            ref |= set(re.findall(r"^func (?:\([^)]*\)\s*)?(\w+)\(", code, flags=re.M))
-            ref |= set(re.findall(r"^type (\w+)\b", code, flags=re.M))
-            ref |= set(re.findall(r"^(?:var|const)\s+(\w+)", code, flags=re.M))
-            for blk in re.findall(r"^(?:const|var) \((.*?)^\)", code, flags=re.M | re.S):
-                ref |= set(re.findall(r"^\s*(\w+)", blk, flags=re.M))
+    """Every top-level identifier (and method name) of the reference's
+    package header, in any file, differs from the shim's."""
+    ref = set(_ref_go()["header_all"])
     assert CHECKSUM_GO_NAMES <= ref
     code = _go_code(open(GO_SHIM).read())
     mine = set(re.findall(r"^func (\w+)\(", code, flags=re.M)) | set(re.findall(r"^type (\w+)\b", code, flags=re.M))
@@ -316,7 +316,7 @@ def test_go_caller_files_pair_up_and_use_only_what_exists():
         assert f"\n\n// +build {tag}\n\npackage {pkg}\n" in raw, rel
         by_pkg.setdefault(pkg, []).append((tag, _signatures(code), code))
         for name in set(re.findall(r"\bheader\.(\w+)", code)):
-            assert name in shim or name in REF_HEADER_NAMES or not os.path.isdir("/root/reference"), (rel, name)
+            assert name in shim or name in REF_HEADER_NAMES, (rel, name)
         for name in set(re.findall(r"\btcpip\.(RXChecksum\w*)", code)):
             assert re.search(rf"\b{name}\b", added), (rel, name)
     for rel, pkg in GO_SHARED.items():
@@ -326,7 +326,7 @@ def test_go_caller_files_pair_up_and_use_only_what_exists():
             assert not re.search(pat, code), (rel, pat)
         assert "+build" not in raw and f"\npackage {pkg}\n" in raw, rel
         for name in set(re.findall(r"\bheader\.(\w+)", code)):
-            assert name in REF_HEADER_NAMES or not os.path.isdir("/root/reference"), (rel, name)  # reference only
+            assert name in REF_HEADER_NAMES, (rel, name)  # reference only
     for pkg, files in by_pkg.items():
         (t1, s1, c1), (t2, s2, c2) = files
         assert t1.replace("!", "") == t2.replace("!", "") and t1 != t2
@@ -339,38 +339,35 @@ def test_go_caller_files_pair_up_and_use_only_what_exists():
 
 
 def _ref_names(d):
-    out = set()
-    for fn in os.listdir(d):
-        if fn.endswith(".go") and not fn.endswith("_test.go"):
-            out |= _top_level(_go_code(open(os.path.join(d, fn)).read()))
-    return out
+    """The top-level names of the reference's package directory `d`."""
+    return set(_ref_go()["names"][d])
 
 
-REF_HEADER_NAMES = _ref_names("/root/reference/tcpip/header") if os.path.isdir("/root/reference/tcpip/header") \
-    else set()
+REF_HEADER_NAMES = _ref_names("tcpip/header")
 
 
-def test_go_patch_applies_to_the_reference_and_adds_no_colliding_names(tmp_path):
-    """go/netstack-hipcsum.patch applies cleanly to the reference's files
-    (patch --dry-run on a copy), and the caller files' top-level names are
-    new in their packages."""
-    if not os.path.isdir("/root/reference/tcpip"):
-        pytest.skip("reference tree absent")
-    import shutil
+def test_go_patch_applies_to_the_reference_and_adds_no_colliding_names():
+    """go/netstack-hipcsum.patch applies cleanly to the reference's files:
+    every hunk's old side (its context and removed lines) is, digest for
+    digest, what the reference's file holds where the hunk applies
+    (tests/golden/ref_go.json: no fuzz, no failed hunk), and the caller
+    files' top-level names are new in their packages."""
+    from make_ref_go import digest, patch_hunks
 
-    files = re.findall(r"^\+\+\+ b/(\S+)", open(GO_PATCH).read(), flags=re.M)
+    text = open(GO_PATCH).read()
+    files = re.findall(r"^\+\+\+ b/(\S+)", text, flags=re.M)
     assert set(files) == {"tcpip/packet_buffer.go", "tcpip/transport/tcp/segment.go",
                           "tcpip/transport/tcp/connect.go", "tcpip/network/ipv4/ipv4.go",
                           "tcpip/link/fdbased/packet_dispatchers.go"}
-    for f in files:
-        os.makedirs(tmp_path / os.path.dirname(f), exist_ok=True)
-        shutil.copy(os.path.join("/root/reference", f), tmp_path / f)
-    r = subprocess.run(["patch", "-p1", "--dry-run", "-i", GO_PATCH], cwd=tmp_path, capture_output=True, text=True)
-    assert r.returncode == 0 and "FAILED" not in r.stdout and "fuzz" not in r.stdout, r.stdout + r.stderr
+    hunks, recorded = patch_hunks(text), _ref_go()["patch_hunks"]
+    assert len(hunks) == len(recorded) == text.count("\n@@ ") and {h[0] for h in hunks} == set(files)
+    for (name, start, old), rec in zip(hunks, recorded):
+        assert (name, start, len(old)) == (rec["file"], rec["old_start"], rec["old_lines"]), (name, start)
+        assert rec["applies_at"] >= 1 and digest(old) == rec["sha256"], (name, start)
     for rel, (pkg, _) in GO_CALLERS.items():
         d = {"tcp": "tcpip/transport/tcp", "fdbased": "tcpip/link/fdbased"}[pkg]
         mine = _top_level(_go_code(open(os.path.join(ROOT, rel)).read()))
-        assert mine and not (mine & _ref_names(os.path.join("/root/reference", d))), (rel, mine)
+        assert mine and not (mine & _ref_names(d)), (rel, mine)
 
 
 def test_latency_bounds_are_collected_after_every_parity_test():
@@ -498,8 +495,7 @@ def test_go_gate_tests_open_the_gates_and_compare_with_the_reference():
         for fn in tested:
             assert re.search(rf"\b{fn}\(", code), (rel, fn)
         for name in set(re.findall(r"\bheader\.(\w+)", code)):
-            assert name in _top_level(shim) or name in REF_HEADER_NAMES or not os.path.isdir("/root/reference"), \
-                (rel, name)
+            assert name in _top_level(shim) or name in REF_HEADER_NAMES, (rel, name)
 
 
 def test_go_tx_host_test_compares_with_the_reference_go():
@@ -522,6 +518,5 @@ def test_go_tx_host_test_compares_with_the_reference_go():
     body = re.search(r"^func fillTCPBatchGo\(.*?^}", shim, flags=re.M | re.S).group(0)
     for ref in ("PseudoHeaderChecksum(", "ChecksumVVWithOffset(", "tcp.CalculateChecksum(", "ip.CalculateChecksum()"):
         assert ref in body, ref
-        if os.path.isdir("/root/reference/tcpip/header"):
-            assert ref.split("(")[0].split(".")[-1] in REF_HEADER_NAMES | {"CalculateChecksum"}, ref
+        assert ref.split("(")[0].split(".")[-1] in REF_HEADER_NAMES | {"CalculateChecksum"}, ref
     assert "C.ns_csum_tcp_tx_host(" in shim and "ns_csum_tcp_tx_host" in declared_symbols()

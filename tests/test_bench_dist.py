@@ -227,6 +227,49 @@ def test_cfg8_defaults_to_the_structured_tx_fill():
     assert g["pay_off"] + g["size"] == total and g["tcp_at"] + g["tcp_len"] == g["slot"]
 
 
+def test_plain_run_leaves_checks_and_cpu_legs_to_full(monkeypatch):
+    """A plain run times the steps only: the parity sample, the CPU legs and
+    the calibrations belong to --full, where --no-cpu / --no-parity still
+    switch the legs off one by one."""
+    import bench
+
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert not a.full and a.no_cpu and a.no_parity and a.steps == 7 and a.dump_outputs is None
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full and not a.no_cpu and not a.no_parity and a.dump_outputs == "d"
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-cpu"])
+    a = bench.parse()
+    assert a.full and a.no_cpu and not a.no_parity
+
+
+def test_dump_outputs_writes_exact_floats_and_a_fixed_sample(tmp_path, monkeypatch):
+    """--dump-outputs: u8 / u16 results (the engine's int16 tensors are u16
+    sums) as float32, exact; an output above DUMP_WHOLE elements as the same
+    DUMP_SAMPLE positions on every run, the positions beside it."""
+    import torch
+
+    import bench
+
+    monkeypatch.setattr(bench, "DUMP_WHOLE", 1000)
+    monkeypatch.setattr(bench, "DUMP_SAMPLE", 64)
+    sums = np.arange(65536 - 500, 65536, dtype=np.uint16)
+    big = (np.arange(5000) % 251).astype(np.uint8)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"sums": torch.from_numpy(sums.view(np.int16).copy()), "big": big})
+    got = np.load(tmp_path / "a" / "sums.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, sums.astype(np.float32)) and got.max() == 65535.0
+    idx = np.load(tmp_path / "a" / "big.index.npy")
+    smp = np.load(tmp_path / "a" / "big.npy")
+    assert idx.dtype == np.float64 and idx.shape == (64,) and (np.diff(idx) >= 0).all()
+    assert smp.dtype == np.float32 and np.array_equal(smp, big[idx.astype(np.int64)].astype(np.float32))
+    for fn in ("sums.npy", "big.npy", "big.index.npy"):
+        assert np.array_equal(np.load(tmp_path / "a" / fn), np.load(tmp_path / "b" / fn))
+    bench.dump_outputs(None, {"sums": sums})  # no directory, nothing written
+    assert sorted(os.listdir(tmp_path)) == ["a", "b"]
+
+
 @pytest.mark.parametrize("calls", [1, 7, 23832, 1 << 20])
 def test_tx_calls_tile_the_batch(calls):
     """bench.py --mode host --config 8 --tx-calls K cuts cfg8's geometry into

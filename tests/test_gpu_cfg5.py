@@ -87,7 +87,7 @@ def test_bench_multi_rank_with_the_hip_engine(config, world):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world),
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
            os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--config", str(config), "--steps", "3",
-           "--warmup", "1", "--no-cpu", "--dist-backend", "gloo"]
+           "--warmup", "1", "--full", "--no-cpu", "--dist-backend", "gloo"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
