@@ -42,6 +42,11 @@
  *   ipv6.go:168-188, header/ipv6.go:207-222), segment.parse
  *   (tcp/segment.go:145-181), handleICMP                         -> ns_csum_rx_ring
  *   ... for a ring in host memory                                 -> ns_csum_rx_ring_host
+ *   the checksums a link with CapabilityTXChecksumOffload owes a batch of
+ *   complete outgoing frames (link/fdbased/endpoint.go:443-556; TCP and UDP
+ *   leave their fields zero then, tcp/connect.go:661, udp/endpoint.go:809),
+ *   parsed and filled on the device                               -> ns_csum_tx_ring
+ *   ... for a ring in host memory                                 -> ns_csum_tx_ring_host
  *
  * Semantics (bit-exact with checksum.go, including its un-folded uint32 wrap for
  * buffers > 128 KiB): every descriptor d is one calculateChecksum call over
@@ -74,7 +79,9 @@ extern "C" {
                                   7: ns_csum_tcp_tx_multi;
                                   8: ns_csum_rx_ring, ns_csum_set_tx_tuning;
                                   9: ns_csum_tcp_tx_host, _host_multi,
-                                     ns_csum_rx_ring_host, ns_csum_rx_bufs */
+                                     ns_csum_rx_ring_host, ns_csum_rx_bufs;
+                                     (still 9: two symbols added, nothing
+                                     changed) ns_csum_tx_ring, _tx_ring_host */
 
 /* ---- status codes ------------------------------------------------------- */
 #define NS_OK 0
@@ -490,6 +497,73 @@ int ns_csum_rx_bufs(ns_csum_ctx* ctx, const uint8_t* d_arena, uint64_t arena_byt
 int ns_csum_rx_ring_host(ns_csum_ctx* ctx, const uint8_t* h_arena, uint64_t arena_bytes,
                          const ns_rx_ring* ring, const uint32_t* h_len, uint16_t* h_sums,
                          uint8_t* h_verdict);
+
+/* ---- a transmit ring, filled without host planning -----------------------
+ * The transmit mirror of ns_csum_rx_ring and the device side of a link that
+ * advertises CapabilityTXChecksumOffload: n slots of `stride` bytes from
+ * d_arena + ring_off, slot s holding one complete outgoing frame of d_len[s]
+ * bytes (u32 device memory, counted from the slot's first byte; the frame is
+ * [frame_at, len), its link header link_hdr bytes).  The kernel parses every
+ * frame itself and stores its checksum fields into the arena.
+ * Gate: a slot is NS_TXR_MALFORMED, and is left byte for byte as it was,
+ * exactly where ns_csum_rx_ring with first_view = 0 gives NS_PKB_MALFORMED: a
+ * length over the stride (counted by ns_csum_sync), a frame of no more than
+ * link_hdr bytes, IPv4 / IPv6 IsValid against the whole frame, the
+ * bad-fragment rules, the transport minimum sizes (TCP 20 with DataOffset in
+ * [20, size], UDP 8, ICMPv4 8, ICMPv6 8).  The transport range is
+ * [IHL*4, TotalLength) / [40, 40 + PayloadLength); frame bytes past it
+ * (Ethernet padding) are never summed.
+ * Fill: both fields are read as zero whatever they hold (a reused ring needs
+ * no clearing; a second call changes nothing).
+ *   IPv4 (unless NS_TXR_L4_ONLY): +10 = ^Checksum(ip[:IHL*4]) (ipv4.go:236,
+ *     fragments :159-160);
+ *   TCP +16 (tcp/connect.go:653-663); UDP +6, the datagram as one view, a sum
+ *     of 0xffff writing 0x0000 as the reference does (udp/endpoint.go:808-815);
+ *   ICMPv4 of any type +2 (ipv4/icmp.go:99-100); ICMPv6 +2 (icmpv6.go:202-221);
+ *   the pseudo-header length of TCP, UDP and ICMPv6 is uint16(transport size).
+ * d_status[s] (u8, or NULL): NS_TXR_L4 where the transport field was written
+ * (and, by default, the IPv4 field of an IPv4 packet), NS_TXR_L3 where only
+ * the IPv4 field was (a fragment, another protocol; never under
+ * NS_TXR_L4_ONLY), NS_TXR_NONE where nothing was (a non-IP EtherType, IPv6
+ * with another next header, IPv4 without a summed transport under
+ * NS_TXR_L4_ONLY), NS_TXR_MALFORMED.  d_sums (2n u16, or NULL): [2s] the IPv4
+ * header sum where its field was written, [2s+1] the transport sum where its
+ * field was, both un-complemented, 0 elsewhere.  Both outputs may be NULL: the
+ * stores are the result, and the only arena bytes that ever change are these
+ * 2-byte fields.  Asynchronous on `stream`; no scratch, no host work per
+ * packet.
+ * NS_EINVAL: NULL ctx (before any device call), d_arena + ring_off or stride
+ * not 16-B aligned, stride 0 or >= 2^24, frame_at + link_hdr odd or
+ * frame_at >= stride, link_hdr not 0 or 14, unknown flags, pad != 0, NULL
+ * d_len (n > 0).  NS_ERANGE: the ring past the arena.                       */
+typedef struct ns_tx_ring {
+  uint64_t ring_off;   /* arena offset of slot 0                         */
+  uint64_t stride;     /* bytes per slot                                 */
+  uint32_t n;          /* slots                                          */
+  uint16_t frame_at;   /* where the link frame starts in a slot          */
+  uint16_t link_hdr;   /* 0 (TUN) or 14 (Ethernet)                       */
+  uint32_t flags;      /* NS_TXR_L4_ONLY or 0                            */
+  uint32_t pad;        /* 0                                              */
+} ns_tx_ring;          /* 32 bytes */
+#define NS_TXR_L4_ONLY 0x1u  /* leave the IPv4 header checksum to the host */
+#define NS_TXR_NONE 0u
+#define NS_TXR_L4 1u
+#define NS_TXR_L3 2u
+#define NS_TXR_MALFORMED 3u
+int ns_csum_tx_ring(ns_csum_ctx* ctx, uint8_t* d_arena, uint64_t arena_bytes,
+                    const ns_tx_ring* ring, const uint32_t* d_len, uint16_t* d_sums,
+                    uint8_t* d_status, void* stream);
+/* The same ring in HOST memory (the frames a link endpoint queued for
+ * sendmmsg): host pointers, the ring's own alignment free.  Whole slots go
+ * to the device in chunks (up to the context's staging size), four in
+ * flight; the kernel fills the staged copy and reports status, sums and where
+ * each transport field lies through mapped memory, and the fields are then
+ * written into h_arena from that report (each store re-checked against the
+ * slot's length and stride).  No host parsing.  Synchronous; shares the host
+ * pipeline as ns_csum_rx_ring_host does.  Errors as for ns_csum_tx_ring.    */
+int ns_csum_tx_ring_host(ns_csum_ctx* ctx, uint8_t* h_arena, uint64_t arena_bytes,
+                         const ns_tx_ring* ring, const uint32_t* h_len, uint16_t* h_sums,
+                         uint8_t* h_status);
 
 /* header.ChecksumCombine(a, b)                     checksum.go:104-107      */
 uint16_t ns_csum_combine(uint16_t a, uint16_t b);

@@ -45,7 +45,8 @@ EXPORTED = (
     "ns_csum_stage_acquire", "ns_csum_stage_release", "ns_csum_packet_buffers",
     "ns_csum_stream_release", "ns_csum_scratch_count", "ns_csum_get_stats", "ns_csum_tcp_tx",
     "ns_csum_tcp_tx_multi", "ns_csum_rx_ring", "ns_csum_set_tx_tuning", "ns_csum_tcp_tx_host",
-    "ns_csum_tcp_tx_host_multi", "ns_csum_rx_ring_host", "ns_csum_rx_bufs",
+    "ns_csum_tcp_tx_host_multi", "ns_csum_rx_ring_host", "ns_csum_rx_bufs", "ns_csum_tx_ring",
+    "ns_csum_tx_ring_host",
 )
 NS_PIECE_RESTART = 0x1
 NS_PIECE_END = 0x2
@@ -55,6 +56,11 @@ NS_PKB_INVALID = 0
 NS_PKB_VALID = 1
 NS_PKB_UNCHECKED = 2
 NS_PKB_MALFORMED = 3
+NS_TXR_L4_ONLY = 0x1
+NS_TXR_NONE = 0
+NS_TXR_L4 = 1
+NS_TXR_L3 = 2
+NS_TXR_MALFORMED = 3
 
 
 class NativeLibraryError(RuntimeError):
@@ -122,6 +128,13 @@ class NsRxRing(ctypes.Structure):
                 ("first_view", ctypes.c_uint32), ("flags", ctypes.c_uint32)]
 
 
+class NsTxRing(ctypes.Structure):
+    """ns_tx_ring: a transmit ring of fixed-stride slots (ns_csum_tx_ring)."""
+    _fields_ = [("ring_off", ctypes.c_uint64), ("stride", ctypes.c_uint64), ("n", ctypes.c_uint32),
+                ("frame_at", ctypes.c_uint16), ("link_hdr", ctypes.c_uint16),
+                ("flags", ctypes.c_uint32), ("pad", ctypes.c_uint32)]
+
+
 NS_TX_TCP_PARTIAL = 0x1
 NS_TX_TCP_NONE = 0x2
 NS_TX_FIELDS_ONLY = 0x4
@@ -134,7 +147,7 @@ class NsOpts(ctypes.Structure):
 
 assert ctypes.sizeof(NsPktDesc) == 16 and ctypes.sizeof(NsSeg) == 24 and ctypes.sizeof(NsPiece) == 24
 assert ctypes.sizeof(NsPktBuf) == 40 and ctypes.sizeof(NsStats) == 13 * 8 and ctypes.sizeof(NsTcpTx) == 48
-assert ctypes.sizeof(NsRxRing) == 32
+assert ctypes.sizeof(NsRxRing) == 32 and ctypes.sizeof(NsTxRing) == 32
 
 _lock = threading.Lock()
 _lib = None
@@ -180,6 +193,8 @@ def _declare(lib):
         "ns_csum_rx_ring": (c.c_int, [vp, u8p, c.c_uint64, c.POINTER(NsRxRing), vp, vp, vp, vp]),
         "ns_csum_rx_ring_host": (c.c_int, [vp, u8p, c.c_uint64, c.POINTER(NsRxRing), vp, vp, vp]),
         "ns_csum_rx_bufs": (c.c_int, [vp, u8p, c.c_uint64, c.POINTER(NsRxRing), vp, vp, vp, vp, vp]),
+        "ns_csum_tx_ring": (c.c_int, [vp, u8p, c.c_uint64, c.POINTER(NsTxRing), vp, vp, vp, vp]),
+        "ns_csum_tx_ring_host": (c.c_int, [vp, u8p, c.c_uint64, c.POINTER(NsTxRing), vp, vp, vp]),
         "ns_csum_set_tx_tuning": (c.c_int, [vp, c.c_uint32, c.c_uint32, c.c_uint32, c.c_uint32]),
         "ns_csum_tcp_tx_host": (c.c_int, [vp, u8p, c.c_uint64, c.POINTER(NsTcpTx), c.c_uint32, vp]),
         "ns_csum_tcp_tx_host_multi": (c.c_int, [c.POINTER(vp), c.c_uint32, u8p, c.c_uint64, c.POINTER(NsTcpTx),

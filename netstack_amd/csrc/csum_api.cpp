@@ -1142,6 +1142,83 @@ int run_rx_host(ns_csum_ctx* ctx, const uint8_t* h_arena, const ns_rx_ring& r, c
   return rc;
 }
 
+// ns_csum_tx_ring_host's pipeline, run_rx_host's shape: the ring in chunks of
+// whole slots, nslots in flight on the host pipeline's streams.  Per chunk:
+// the slots and their lengths go to the device, tx_ring parses them there,
+// fills the staged copy and writes status, sums and each transport field's
+// place straight to mapped pinned memory; when the chunk is done the fields
+// are written into the caller's ring from that report (nsh::tx_ring_patch)
+// while later chunks are in flight.  No host parsing, no copy back.
+int run_tx_ring_host(ns_csum_ctx* ctx, uint8_t* h_arena, const ns_tx_ring& r, const uint32_t* h_len,
+                     uint16_t* h_sums, uint8_t* h_status) {
+  const uint32_t nslots = ctx->nslots;
+  const uint32_t per = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(1, ctx->staging / r.stride), 1u << 24);
+  struct Pending {
+    bool live = false;
+    uint32_t first = 0, count = 0;
+  } pend[kMaxHostSlots];
+  auto finish = [&](uint32_t sl) -> int {
+    if (!pend[sl].live) return NS_OK;
+    pend[sl].live = false;
+    HIP_TRY(hipEventSynchronize(ctx->done[sl]));
+    const uint32_t first = pend[sl].first, cnt = pend[sl].count;
+    // status in the mapped buffer's first cnt bytes, the fields' places after
+    nsh::tx_ring_patch(h_arena + r.ring_off, r.stride, (uint32_t)r.frame_at + r.link_hdr, h_len, first, cnt,
+                       ctx->h_out[sl].p, ctx->h_verd[sl].p + cnt);
+    if (h_sums) std::memcpy(h_sums + 2 * (uint64_t)first, ctx->h_out[sl].p, 4 * (size_t)cnt);
+    if (h_status) std::memcpy(h_status + first, ctx->h_verd[sl].p, cnt);
+    return NS_OK;
+  };
+  auto enqueue = [&](uint32_t first, uint32_t cnt, uint32_t sl) -> int {
+    int rc;
+    const uint64_t bytes = (uint64_t)cnt * r.stride;
+    if ((rc = ctx->d_arena[sl].ensure(bytes)) != NS_OK) return rc;
+    if ((rc = ctx->d_len[sl].ensure(cnt)) != NS_OK) return rc;
+    if ((rc = ctx->h_out[sl].ensure(2 * (size_t)cnt)) != NS_OK) return rc;
+    if ((rc = ctx->h_verd[sl].ensure(2 * (uint64_t)cnt)) != NS_OK) return rc;
+    hipStream_t s = ctx->stream[sl];
+    HIP_TRY(hipMemcpyAsync(ctx->d_arena[sl].p, h_arena + r.ring_off + (uint64_t)first * r.stride, bytes,
+                           hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(ctx->d_len[sl].p, h_len + first, 4 * (size_t)cnt, hipMemcpyHostToDevice, s));
+    nsk::TxRingGeo geo{};
+    geo.ring = (uint64_t)(uintptr_t)ctx->d_arena[sl].p;
+    geo.stride = r.stride;
+    geo.len = ctx->d_len[sl].p;
+    geo.sums = ctx->h_out[sl].dev;
+    geo.status = ctx->h_verd[sl].dev;
+    geo.at = ctx->h_verd[sl].dev + cnt;
+    geo.err = ctx->d_err;
+    geo.n = cnt;
+    geo.frame_at = r.frame_at;
+    geo.link = r.link_hdr;
+    geo.flags = r.flags;
+    HIP_TRY(nsk::launch_tx_ring(geo, s));
+    HIP_TRY(hipEventRecord(ctx->done[sl], s));
+    return NS_OK;
+  };
+  int rc = NS_OK;
+  uint32_t slot = 0;
+  for (uint64_t f = 0; f < r.n; f += per) {  // 64-bit: first + per may pass 2^32
+    const uint32_t first = (uint32_t)f;
+    const uint32_t cnt = (uint32_t)std::min<uint64_t>(per, r.n - f);
+    if ((rc = finish(slot)) != NS_OK) break;
+    if ((rc = enqueue(first, cnt, slot)) != NS_OK) {
+      (void)hipStreamSynchronize(ctx->stream[slot]);
+      (void)hipGetLastError();
+      break;
+    }
+    pend[slot].live = true;
+    pend[slot].first = first;
+    pend[slot].count = cnt;
+    slot = (slot + 1) % nslots;
+  }
+  for (uint32_t k = 0; k < nslots; ++k) {
+    const int e = finish((slot + k) % nslots);
+    if (rc == NS_OK) rc = e;
+  }
+  return rc;
+}
+
 // Caller-acquired staging (ns_csum_stage_acquire): mapped pinned buffers a
 // caller fills itself — the Go shim, which may not hand C memory holding Go
 // pointers to the library, copies its views there once.  Gathers whose bytes
@@ -1888,6 +1965,49 @@ int ns_csum_rx_ring_host(ns_csum_ctx* ctx, const uint8_t* h_arena, uint64_t aren
   std::lock_guard<std::mutex> lk(ctx->pmu);
   DeviceGuard g(ctx->device);
   return run_rx_host(ctx, h_arena, r, h_len, h_sums, h_verdict);
+}
+
+int ns_csum_tx_ring(ns_csum_ctx* ctx, uint8_t* d_arena, uint64_t arena_bytes, const ns_tx_ring* ring,
+                    const uint32_t* d_len, uint16_t* d_sums, uint8_t* d_status, void* stream) {
+  if (!ctx || !ring || (arena_bytes && !d_arena)) return NS_EINVAL;
+  const ns_tx_ring& r = *ring;
+  if (r.n && !d_len) return NS_EINVAL;
+  const uint64_t base = (uint64_t)(uintptr_t)d_arena;
+  const int vr = nsh::tx_ring_plan(r, base, arena_bytes);
+  if (vr != NS_OK) return vr;
+  if (r.n == 0) return NS_OK;
+  DeviceGuard g(ctx->device);
+  nsk::TxRingGeo geo{};
+  geo.ring = base + r.ring_off;
+  geo.stride = r.stride;
+  geo.len = d_len;
+  geo.sums = d_sums;
+  geo.status = d_status;
+  geo.err = ctx->d_err;
+  geo.n = r.n;
+  geo.frame_at = r.frame_at;
+  geo.link = r.link_hdr;
+  geo.flags = r.flags;
+  HIP_TRY(nsk::launch_tx_ring(geo, (hipStream_t)stream));
+  return NS_OK;
+}
+
+int ns_csum_tx_ring_host(ns_csum_ctx* ctx, uint8_t* h_arena, uint64_t arena_bytes, const ns_tx_ring* ring,
+                         const uint32_t* h_len, uint16_t* h_sums, uint8_t* h_status) {
+  if (!ctx || !ring || (arena_bytes && !h_arena)) return NS_EINVAL;
+  const ns_tx_ring& r = *ring;
+  if (r.n && !h_len) return NS_EINVAL;
+  if (r.ring_off > arena_bytes) return NS_ERANGE;
+  // the slots go to 16-B-aligned staging: the host ring's own alignment is free
+  ns_tx_ring r0 = r;
+  r0.ring_off = 0;
+  const int vr = nsh::tx_ring_plan(r0, 0, arena_bytes - r.ring_off);
+  if (vr != NS_OK) return vr;
+  CallClock clk(ctx);
+  if (r.n == 0) return NS_OK;
+  std::lock_guard<std::mutex> lk(ctx->pmu);
+  DeviceGuard g(ctx->device);
+  return run_tx_ring_host(ctx, h_arena, r, h_len, h_sums, h_status);
 }
 
 int ns_csum_batch_host(ns_csum_ctx* ctx, const uint8_t* h_arena, uint64_t arena_bytes,

@@ -173,4 +173,26 @@ struct RxGeo {
 };
 hipError_t launch_rx_ring(const RxGeo& g, hipStream_t stream);
 
+// A transmit ring filled on the device (tx_ring.hip, ns_csum_tx_ring): the
+// ring's geometry as RxGeo's (one view, no buffer list), validated by the
+// caller.  Per slot s: the frame's length len[s]; the checksum fields are
+// stored into the ring; status[s] (NS_TXR_*), sums[2s] (the IPv4 header's
+// sum, 0 where its field was not written) and sums[2s + 1] (the transport
+// sum), or nullptr.  at[s] (or nullptr; the host ring's patch list): where
+// the transport field written lies, in bytes from the IP packet's first byte
+// (22 ... 76), 0 where none was.
+struct TxRingGeo {
+  uint64_t ring, stride;
+  const uint32_t* len;
+  uint16_t* sums;
+  uint8_t* status;
+  uint8_t* at;
+  unsigned long long* err;
+  uint32_t n;
+  uint32_t frame_at;  // bytes before the link frame in a slot
+  uint32_t link;      // 0: the frame is the IP packet; 14: Ethernet
+  uint32_t flags;     // NS_TXR_L4_ONLY
+};
+hipError_t launch_tx_ring(const TxRingGeo& g, hipStream_t stream);
+
 }  // namespace nsk

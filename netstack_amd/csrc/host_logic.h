@@ -1067,4 +1067,43 @@ inline int rx_plan(const ns_rx_ring& r, uint64_t base, uint64_t arena_bytes) {
   return NS_OK;
 }
 
+// ns_csum_tx_ring's geometry, validated: rx_plan's rules without first_view.
+inline int tx_ring_plan(const ns_tx_ring& r, uint64_t base, uint64_t arena_bytes) {
+  if ((r.flags & ~NS_TXR_L4_ONLY) || r.pad) return NS_EINVAL;
+  ns_rx_ring rr{};
+  rr.ring_off = r.ring_off;
+  rr.stride = r.stride;
+  rr.n = r.n;
+  rr.frame_at = r.frame_at;
+  rr.link_hdr = r.link_hdr;
+  return rx_plan(rr, base, arena_bytes);
+}
+
+// ns_csum_tx_ring_host: the fields of slots [first, first + count) written
+// into the caller's ring (`ring` = its slot 0, `stride` bytes per slot) from
+// what the device reported for the staged copy: sums[2k], sums[2k + 1] (k
+// from `first`: the chunk's own arrays) and at[k], the transport field's
+// offset from the IP packet's first byte (0: none).  The IPv4 field is at
+// +10 exactly when sums[2k] != 0.  The device's bytes are never trusted to
+// stay inside the ring: every store is re-checked against the slot's length
+// and the stride, and skipped otherwise.  Returns the stores made.
+inline uint64_t tx_ring_patch(uint8_t* ring, uint64_t stride, uint32_t pre, const uint32_t* len, uint32_t first,
+                              uint32_t count, const uint16_t* sums, const uint8_t* at) {
+  uint64_t stores = 0;
+  for (uint32_t k = 0; k < count; ++k) {
+    const uint64_t s = (uint64_t)first + k, L = len[s];
+    uint8_t* ip = ring + s * stride + pre;
+    auto put = [&](uint64_t off, uint16_t sum) {
+      if (L > stride || (uint64_t)pre + off + 2 > L) return;
+      const uint16_t f = (uint16_t)~sum;
+      ip[off] = (uint8_t)(f >> 8);
+      ip[off + 1] = (uint8_t)f;
+      ++stores;
+    };
+    if (sums[2 * k]) put(10, sums[2 * k]);
+    if (at[k]) put(at[k], sums[2 * k + 1]);
+  }
+  return stores;
+}
+
 }  // namespace nsh

@@ -265,6 +265,60 @@ class Engine:
                                          _ptr(verdict)), "ns_csum_rx_ring_host")
         return verdict[:n], sums[:2 * n]
 
+    def tx_ring(self, arena, ring: dict, lens, sums=None, status=None, stream=None):
+        """Fill the checksum fields of a transmit ring resident in HBM
+        (ns_csum_tx_ring): `arena` a uint8 CUDA tensor holding n slots of
+        `stride` bytes from `ring_off`, each one complete outgoing frame;
+        `ring` the keys of ns_tx_ring (ring_off, stride, n, frame_at,
+        link_hdr, flags); `lens` an int32/uint32 CUDA tensor of the n frame
+        lengths.  The fields are stored into `arena`.  `status` (uint8, n)
+        and `sums` (16-bit, 2n) are allocated when None.  Launches on
+        `stream` (default: torch's current stream) without synchronising;
+        returns (status, sums)."""
+        import torch
+
+        n = int(ring["n"])
+        if not (arena.is_cuda and lens.is_cuda):
+            raise ValueError("arena and lens must be device tensors")
+        if lens.element_size() != 4 or lens.numel() < n or not lens.is_contiguous():
+            raise ValueError("lens must be a contiguous tensor of n 32-bit lengths")
+        if status is None:
+            status = torch.empty(max(n, 1), dtype=torch.uint8, device=arena.device)
+        if sums is None:
+            sums = torch.empty(max(2 * n, 1), dtype=torch.int16, device=arena.device)
+        if not status.is_cuda or status.element_size() != 1 or status.numel() < n:
+            raise ValueError("status must be a device tensor of n bytes")
+        if not sums.is_cuda or sums.element_size() != 2 or sums.numel() < 2 * n:
+            raise ValueError("sums must be a device tensor of 2n 16-bit sums")
+        r = _tx_ring_struct(ring)
+        if stream is None:
+            stream = torch.cuda.current_stream(arena.device)
+        check(lib().ns_csum_tx_ring(self._h, arena.data_ptr(), arena.numel() * arena.element_size(),
+                                    ctypes.byref(r), lens.data_ptr(), sums.data_ptr(), status.data_ptr(),
+                                    getattr(stream, "cuda_stream", stream)), "ns_csum_tx_ring")
+        return status, sums
+
+    def tx_ring_host(self, arena, ring: dict, lens):
+        """Fill the checksum fields of a transmit ring in HOST memory
+        (ns_csum_tx_ring_host): `arena` a writable, contiguous uint8 numpy
+        array (pageable, or a stage from stage_acquire), `ring` as for
+        tx_ring, `lens` the n frame lengths (uint32).  Synchronous: the
+        fields are written into `arena` in place; returns (status, sums) as
+        numpy arrays of n bytes and 2n u16."""
+        if not (isinstance(arena, np.ndarray) and arena.dtype == np.uint8 and arena.flags.c_contiguous
+                and arena.flags.writeable):
+            raise ValueError("arena must be a writable, contiguous uint8 numpy array")
+        n = int(ring["n"])
+        ln = np.ascontiguousarray(lens, dtype=np.uint32)
+        if ln.size < n:
+            raise ValueError("lens must hold n frame lengths")
+        status = np.zeros(max(n, 1), dtype=np.uint8)
+        sums = np.zeros(max(2 * n, 1), dtype=np.uint16)
+        r = _tx_ring_struct(ring)
+        check(lib().ns_csum_tx_ring_host(self._h, _ptr(arena), arena.size, ctypes.byref(r), _ptr(ln), _ptr(sums),
+                                         _ptr(status)), "ns_csum_tx_ring_host")
+        return status[:n], sums[:2 * n]
+
     def stream_release(self, stream) -> None:
         """Free the scratch this context keeps for `stream` (a torch.cuda.Stream
         or a raw hipStream_t) after its last launch (ns_csum_stream_release);
@@ -394,6 +448,12 @@ def tx_table(geos, mode: str = "full"):
                               geo["addr_sum"] if "addr_sum" in geo else addr_sum(bytes(geo["src"]), bytes(geo["dst"])),
                               geo.get("protocol", 6), _TX_MODES[geo.get("mode", mode)])
     return arr
+
+
+def _tx_ring_struct(ring: dict):
+    return _lib.NsTxRing(int(ring.get("ring_off", 0)), int(ring["stride"]), int(ring["n"]),
+                         int(ring.get("frame_at", 0)), int(ring.get("link_hdr", 0)), int(ring.get("flags", 0)),
+                         int(ring.get("pad", 0)))
 
 
 def _tx_host_args(arena, geos, mode):
