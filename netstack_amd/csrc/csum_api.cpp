@@ -306,7 +306,7 @@ void bump_max(std::atomic<uint64_t>& m, uint64_t v) {
 // mapped memory, 128K-descriptor chunks (round 5, profiles/r05/host/): 2 /
 // 3 / 4 slots 1.86 / 1.80 / 1.72 ms per call, against 2.03 / 1.90 / 1.88 ms
 // with the D2H copy.
-constexpr uint32_t kMaxHostSlots = 4;
+using nsh::kMaxHostSlots;
 constexpr uint32_t kHostSlots = 4;
 constexpr uint32_t kHostChunkDesc = 1u << 17;
 
@@ -708,11 +708,6 @@ int submit_small(ns_csum_ctx* ctx, SmallReq* req) {
   });
 }
 
-// Host batch core, caller holds ctx->pmu and the device guard.  Pipelines
-// chunks of the descriptor table over the context's slots/streams: H2D of
-// chunk k+1 overlaps the kernel of chunk k.  Chunks never split a
-// NS_DESC_CONT run.
-
 // Whether [p, p + bytes) is page-locked host memory the DMA engines read
 // directly (hipHostMalloc, hipHostRegister, torch pin_memory).  A pageable
 // pointer makes hipPointerGetAttributes fail; that error is cleared so no
@@ -730,108 +725,94 @@ bool host_pinned(const void* p, uint64_t bytes) {
   return true;
 }
 
+// The host DMA pipelines below (caller holds ctx->pmu and the device guard)
+// run their chunks through nsh::run_slots, ctx->nslots in flight, each on
+// its slot's stream and staging: a chunk's H2D copies overlap the kernels of
+// the chunks before it.  Each gives its own `next`, `enqueue` and `finish`
+// (which first waits for the slot's `done` event); `quiesce` is this for all:
+// copies of a chunk whose enqueue failed part-way may be in flight, and the
+// caller's memory and the staging must be idle before returning.  The
+// failure was reported already, so the sticky error is cleared.
+auto quiesce_slot(ns_csum_ctx* ctx) {
+  return [ctx](uint32_t slot) {
+    (void)hipStreamSynchronize(ctx->stream[slot]);
+    (void)hipGetLastError();
+  };
+}
+
+// Host batch core: the descriptor table in chunks that never split a
+// NS_DESC_CONT run.
 int run_host_batch(ns_csum_ctx* ctx, const uint8_t* h_arena, uint64_t arena_bytes,
                    const ns_pkt_desc* h_desc, uint32_t n, uint16_t* h_out,
                    bool chained) {
-  if (n == 0) return NS_OK;
-  const uint64_t budget = ctx->staging;
   // A pinned table goes to the device straight from the caller's memory; a
   // pageable one is copied into pinned staging chunk by chunk first (1M x
   // 64 B: that copy, 16 MB per call on one core, was as long as the chunks'
   // DMA).
   const bool desc_pinned = host_pinned(h_desc, (uint64_t)n * sizeof(ns_pkt_desc));
-  struct Pending {
-    bool live = false;
-    uint32_t first = 0, count = 0;
-  } pend[kMaxHostSlots];
-  const uint32_t nslots = ctx->nslots;
-  // Drain whatever is in flight (on an error return too: the staging
-  // buffers must be idle before the next call reuses them).
-  auto drain = [&](int slot) -> int {
-    for (uint32_t s = 0; s < nslots; ++s) {
-      const int sl = (int)((slot + s) % nslots);
-      if (pend[sl].live) {
-        HIP_TRY(hipEventSynchronize(ctx->done[sl]));
-        std::memcpy(h_out + pend[sl].first, ctx->h_out[sl].p, pend[sl].count * sizeof(uint16_t));
-        pend[sl].live = false;
-      }
-    }
+  struct Chunk {
+    uint32_t first, count;  // descriptors [first, first + count)
+    uint64_t lo, hi;        // their byte span in the arena
+  };
+  // The next chunk (nsh::cut_chunk): at most chunk_desc descriptors and
+  // ctx->staging bytes of span, never inside a chained run; descriptors are
+  // range-checked on the way, so a bad one ends the call mid-pipeline.  1M x
+  // 64 B: 4.27 ms -> 2.15 ms per call with this, the skipped span pass and the
+  // device-side table rebase (profiles/r01/bench_host3.json).
+  uint32_t k = 0;
+  auto next = [&](Chunk* c) -> int {
+    if (k >= n) return nsh::kSlotsDone;
+    uint32_t cut = k;
+    const int rc = nsh::cut_chunk(h_desc, n, k, arena_bytes, ctx->staging, ctx->chunk_desc, chained, &cut, &c->lo,
+                                  &c->hi);
+    if (rc != NS_OK) return rc;
+    c->first = k;
+    c->count = cut - k;
+    k = cut;
     return NS_OK;
   };
-  uint32_t k = 0;
-  int slot = 0;
-  while (k < n) {
-    // The next chunk (nsh::cut_chunk): at most kHostChunkDesc descriptors
-    // and `budget` bytes of span, never inside a chained run; descriptors are
-    // range-checked on the way.  1M x 64 B: 4.27 ms -> 2.15 ms per call with
-    // this, the skipped span pass and the device-side table rebase
-    // (profiles/r01/bench_host3.json).
-    uint32_t cut = k;
-    uint64_t cut_lo = 0, cut_hi = 0;
-    const int crc = nsh::cut_chunk(h_desc, n, k, arena_bytes, budget, ctx->chunk_desc, chained, &cut, &cut_lo,
-                                   &cut_hi);
-    if (crc != NS_OK) {
-      const int rc = drain(slot);
-      return rc != NS_OK ? rc : crc;
+  auto enqueue = [&](const Chunk& c, uint32_t slot) -> int {
+    int rc;
+    const uint32_t cnt = c.count;
+    const uint64_t span = c.hi - c.lo;
+    if ((rc = ctx->d_arena[slot].ensure(std::max<uint64_t>(span, 16))) != NS_OK) return rc;
+    if ((rc = ctx->d_desc[slot].ensure(cnt)) != NS_OK) return rc;
+    if (ctx->host_d2h && (rc = ctx->d_out[slot].ensure(cnt)) != NS_OK) return rc;
+    if (!desc_pinned && (rc = ctx->h_desc[slot].ensure(cnt)) != NS_OK) return rc;
+    if ((rc = ctx->h_out[slot].ensure(cnt)) != NS_OK) return rc;
+    if (chained && (rc = ctx->d_chain[slot].ensure(cnt)) != NS_OK) return rc;
+    // The table goes over verbatim (from the caller's pinned table, or one
+    // memcpy into pinned staging) and is rebased to the chunk on the
+    // device: a per-descriptor rewrite on the CPU was the limit of
+    // small-packet batches.
+    const ns_pkt_desc* hd = h_desc + c.first;
+    if (!desc_pinned) {
+      std::memcpy(ctx->h_desc[slot].p, hd, (size_t)cnt * sizeof(ns_pkt_desc));
+      hd = ctx->h_desc[slot].p;
     }
-    const uint32_t cnt = cut - k;
-    const uint64_t span = cut_hi - cut_lo;
-
-    // Retire the slot's previous chunk before reusing its staging.
-    if (pend[slot].live) {
-      HIP_TRY(hipEventSynchronize(ctx->done[slot]));
-      std::memcpy(h_out + pend[slot].first, ctx->h_out[slot].p, pend[slot].count * sizeof(uint16_t));
-      pend[slot].live = false;
-    }
-    // Everything that can fail for this chunk; on failure the other slot's
-    // transfers are drained before returning (the next call reuses the
-    // pinned buffers they read and write).
-    auto enqueue = [&]() -> int {
-      int rc;
-      if ((rc = ctx->d_arena[slot].ensure(std::max<uint64_t>(span, 16))) != NS_OK) return rc;
-      if ((rc = ctx->d_desc[slot].ensure(cnt)) != NS_OK) return rc;
-      if (ctx->host_d2h && (rc = ctx->d_out[slot].ensure(cnt)) != NS_OK) return rc;
-      if (!desc_pinned && (rc = ctx->h_desc[slot].ensure(cnt)) != NS_OK) return rc;
-      if ((rc = ctx->h_out[slot].ensure(cnt)) != NS_OK) return rc;
-      if (chained && (rc = ctx->d_chain[slot].ensure(cnt)) != NS_OK) return rc;
-      // The table goes over verbatim (from the caller's pinned table, or one
-      // memcpy into pinned staging) and is rebased to the chunk on the
-      // device: a per-descriptor rewrite on the CPU was the limit of
-      // small-packet batches.
-      const ns_pkt_desc* hd = h_desc + k;
-      if (!desc_pinned) {
-        std::memcpy(ctx->h_desc[slot].p, hd, (size_t)cnt * sizeof(ns_pkt_desc));
-        hd = ctx->h_desc[slot].p;
-      }
-      hipStream_t s = ctx->stream[slot];
-      if (span) HIP_TRY(hipMemcpyAsync(ctx->d_arena[slot].p, h_arena + cut_lo, span, hipMemcpyHostToDevice, s));
-      HIP_TRY(hipMemcpyAsync(ctx->d_desc[slot].p, hd, cnt * sizeof(ns_pkt_desc), hipMemcpyHostToDevice, s));
-      HIP_TRY(nsk::launch_rebase(ctx->d_desc[slot].p, cnt, cut_lo, s));
-      // The results go straight to mapped host memory: a D2H copy would sit
-      // on the DMA engine's ring waiting for this kernel, and every later
-      // chunk's H2D copies queue behind it (a rocprofv3 copy trace of cfg3
-      // showed the slots' streams fully serialised that way).
-      uint16_t* dst = ctx->host_d2h ? ctx->d_out[slot].p : ctx->h_out[slot].dev;
-      HIP_TRY(nsk::launch_batch(ctx->d_arena[slot].p, span, ctx->d_desc[slot].p, cnt, dst,
-                                chained ? ctx->d_chain[slot].get(ctx->fold_walk) : nsk::ChainScratch{}, ctx->d_err, s));
-      if (ctx->host_d2h)
-        HIP_TRY(hipMemcpyAsync(ctx->h_out[slot].p, ctx->d_out[slot].p, cnt * sizeof(uint16_t), hipMemcpyDeviceToHost,
-                               s));
-      HIP_TRY(hipEventRecord(ctx->done[slot], s));
-      return NS_OK;
-    };
-    const int rc = enqueue();
-    if (rc != NS_OK) {
-      (void)drain(slot);
-      return rc;
-    }
-    pend[slot].live = true;
-    pend[slot].first = k;
-    pend[slot].count = cnt;
-    k = cut;
-    slot = (int)((slot + 1) % nslots);
-  }
-  return drain(slot);
+    hipStream_t s = ctx->stream[slot];
+    if (span) HIP_TRY(hipMemcpyAsync(ctx->d_arena[slot].p, h_arena + c.lo, span, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(ctx->d_desc[slot].p, hd, cnt * sizeof(ns_pkt_desc), hipMemcpyHostToDevice, s));
+    HIP_TRY(nsk::launch_rebase(ctx->d_desc[slot].p, cnt, c.lo, s));
+    // The results go straight to mapped host memory: a D2H copy would sit
+    // on the DMA engine's ring waiting for this kernel, and every later
+    // chunk's H2D copies queue behind it (a rocprofv3 copy trace of cfg3
+    // showed the slots' streams fully serialised that way).
+    uint16_t* dst = ctx->host_d2h ? ctx->d_out[slot].p : ctx->h_out[slot].dev;
+    HIP_TRY(nsk::launch_batch(ctx->d_arena[slot].p, span, ctx->d_desc[slot].p, cnt, dst,
+                              chained ? ctx->d_chain[slot].get(ctx->fold_walk) : nsk::ChainScratch{}, ctx->d_err, s));
+    if (ctx->host_d2h)
+      HIP_TRY(hipMemcpyAsync(ctx->h_out[slot].p, ctx->d_out[slot].p, cnt * sizeof(uint16_t), hipMemcpyDeviceToHost,
+                             s));
+    HIP_TRY(hipEventRecord(ctx->done[slot], s));
+    return NS_OK;
+  };
+  auto finish = [&](const Chunk& c, uint32_t slot) -> int {
+    HIP_TRY(hipEventSynchronize(ctx->done[slot]));
+    std::memcpy(h_out + c.first, ctx->h_out[slot].p, c.count * sizeof(uint16_t));
+    return NS_OK;
+  };
+  return nsh::run_slots<Chunk>(ctx->nslots, next, enqueue, finish, quiesce_slot(ctx));
 }
 
 inline void put_be16(uint8_t* p, uint32_t v) {
@@ -839,14 +820,6 @@ inline void put_be16(uint8_t* p, uint32_t v) {
   p[1] = (uint8_t)v;
 }
 
-// ns_csum_tcp_tx_host's pipeline over nsh::tx_host_plan's chunks, nslots in
-// flight on the host pipeline's streams.  Per chunk: one H2D copy per merged
-// byte range into the slot's staging, the geometry table, and one
-// tcp_tx_multi launch (fields-only: its stores stay in the staging) whose sums
-// go straight to mapped pinned memory.  When a chunk is done the host writes
-// its fields into the caller's slots from those sums, the values the kernel
-// stores (2 x 2 B per segment instead of copying the slots back), while the
-// later chunks are in flight.
 // A finished chunk's fields, written into the caller's slots from the sums
 // the kernel left in `res` (the values it stores), and its sums to h_out.
 void patch_tx_fields(const nsh::TxHostPlan& plan, const nsh::TxChunk& c, const uint16_t* res, uint8_t* h_arena,
@@ -901,6 +874,18 @@ uint32_t tx_chunk_table(const nsh::TxHostPlan& plan, const nsh::TxChunk& c, uint
 // calls do.  Above that size the DMA pipeline's ~55 GB/s beats the BAR's ~23.
 constexpr uint64_t kHostSmallBytes = 1ull << 20;
 
+// Where a TX chunk's geometry table lies: TxGeo[np] padded to `tab` bytes,
+// then first[np + 1].  The small path puts it behind the chunk's bytes in its
+// stage, at `tab_at`, `need` stage bytes in all; the pipeline uploads the
+// table's need - tab_at bytes on their own.
+struct TxTableLayout {
+  uint64_t tab_at, tab, need;
+  explicit TxTableLayout(const nsh::TxChunk& c)
+      : tab_at((c.staging + 255) & ~255ull),
+        tab(((uint64_t)c.np * sizeof(nsk::TxGeo) + 15) & ~15ull),
+        need(tab_at + tab + ((uint64_t)c.np + 1) * sizeof(uint32_t)) {}
+};
+
 // Completes a small host-path launch on stream s (pmu held): a one-wave
 // kernel behind it stores this call's sequence number into coherent host
 // memory and the caller spins on that word, as the zero-copy passes do (the
@@ -933,10 +918,9 @@ int run_tx_small(ns_csum_ctx* ctx, uint8_t* h_arena, const nsh::TxHostPlan& plan
   int rc = NS_OK;
   if ((rc = ctx->p_res.ensure(4 * c.nout)) != NS_OK) return rc;
   uint16_t* res = reinterpret_cast<uint16_t*>(ctx->p_res.p);
-  const uint64_t tab_at = (c.staging + 255) & ~255ull;
-  const size_t tab = ((size_t)c.np * sizeof(nsk::TxGeo) + 15) & ~(size_t)15;
-  const uint64_t need = tab_at + tab + ((size_t)c.np + 1) * sizeof(uint32_t);
-  BarBuf* st = lease_gather_stage(ctx, &rc, need);
+  const TxTableLayout lay(c);
+  const uint64_t tab_at = lay.tab_at, tab = lay.tab;
+  BarBuf* st = lease_gather_stage(ctx, &rc, lay.need);
   if (!st) return rc;
   for (uint32_t j = c.r0; j < c.r0 + c.nr; ++j) {
     const nsh::TxRange& r = plan.ranges[j];
@@ -965,29 +949,31 @@ int run_tx_small(ns_csum_ctx* ctx, uint8_t* h_arena, const nsh::TxHostPlan& plan
   return NS_OK;
 }
 
+// ns_csum_tcp_tx_host's pipeline over nsh::tx_host_plan's chunks.  Per chunk:
+// one H2D copy per merged byte range into the slot's staging, the geometry
+// table, and one tcp_tx_multi launch (fields-only: its stores stay in the
+// staging) whose sums go straight to mapped pinned memory.  When a chunk is
+// done the host writes its fields into the caller's slots from those sums,
+// the values the kernel stores (2 x 2 B per segment instead of copying the
+// slots back), while the later chunks are in flight.  A plan of one chunk
+// that fits kHostSmallBytes takes the small path instead — within the
+// context's staging budget too: a context created with a small budget sends
+// everything through the pipeline.
 int run_tx_host(ns_csum_ctx* ctx, uint8_t* h_arena, const nsh::TxHostPlan& plan, uint16_t* h_out) {
-  if (plan.chunks.size() == 1 && zero_copy_enabled()) {
-    // (within the context's staging budget too: a context created with a
-    // small budget sends everything through the pipeline)
-    const nsh::TxChunk& c = plan.chunks[0];
-    const uint64_t tab = ((uint64_t)c.np * sizeof(nsk::TxGeo) + 15) & ~15ull;
-    const uint64_t need = ((c.staging + 255) & ~255ull) + tab + 4ull * (c.np + 1);
-    if (need <= std::min<uint64_t>(kHostSmallBytes, ctx->staging)) return run_tx_small(ctx, h_arena, plan, h_out);
-  }
-  const uint32_t nslots = ctx->nslots;
-  int64_t pend[kMaxHostSlots];
-  std::fill(pend, pend + kMaxHostSlots, (int64_t)-1);
-  auto finish = [&](uint32_t sl) -> int {
-    if (pend[sl] < 0) return NS_OK;
-    const nsh::TxChunk& c = plan.chunks[(size_t)pend[sl]];
-    pend[sl] = -1;
-    HIP_TRY(hipEventSynchronize(ctx->done[sl]));
-    patch_tx_fields(plan, c, ctx->h_out[sl].p, h_arena, h_out);
+  if (plan.chunks.size() == 1 && zero_copy_enabled() &&
+      TxTableLayout(plan.chunks[0]).need <= std::min<uint64_t>(kHostSmallBytes, ctx->staging))
+    return run_tx_small(ctx, h_arena, plan, h_out);
+  using Chunk = const nsh::TxChunk*;
+  size_t ci = 0;
+  auto next = [&](Chunk* c) -> int {
+    if (ci == plan.chunks.size()) return nsh::kSlotsDone;
+    *c = &plan.chunks[ci++];
     return NS_OK;
   };
   std::vector<nsk::TxGeo> calls;
   std::vector<uint32_t> first;
-  auto enqueue = [&](const nsh::TxChunk& c, uint32_t sl) -> int {
+  auto enqueue = [&](Chunk cp, uint32_t sl) -> int {
+    const nsh::TxChunk& c = *cp;
     int rc;
     if ((rc = ctx->d_arena[sl].ensure(c.staging + 256)) != NS_OK) return rc;
     if ((rc = ctx->h_out[sl].ensure(2 * c.nout)) != NS_OK) return rc;
@@ -995,8 +981,8 @@ int run_tx_host(ns_csum_ctx* ctx, uint8_t* h_arena, const nsh::TxHostPlan& plan,
     const uint32_t grid = tx_chunk_table(plan, c, (uint64_t)(uintptr_t)ctx->d_arena[sl].p, ctx->h_out[sl].dev,
                                          &calls, &first, &launch);
     if (grid == 0) return NS_EINVAL;  // more than 2^31 tiles
-    const size_t tab = ((size_t)c.np * sizeof(nsk::TxGeo) + 15) & ~(size_t)15;
-    const size_t bytes = tab + first.size() * sizeof(uint32_t);
+    const TxTableLayout lay(c);
+    const size_t tab = (size_t)lay.tab, bytes = (size_t)(lay.need - lay.tab_at);
     if ((rc = ctx->h_txtab[sl].ensure(bytes)) != NS_OK) return rc;
     if ((rc = ctx->d_txtab[sl].ensure(bytes)) != NS_OK) return rc;
     std::memcpy(ctx->h_txtab[sl].p, calls.data(), (size_t)c.np * sizeof(nsk::TxGeo));
@@ -1012,36 +998,53 @@ int run_tx_host(ns_csum_ctx* ctx, uint8_t* h_arena, const nsh::TxHostPlan& plan,
     HIP_TRY(hipEventRecord(ctx->done[sl], s));
     return NS_OK;
   };
-  int rc = NS_OK;
-  uint32_t slot = 0;
-  for (size_t ci = 0; ci < plan.chunks.size(); ++ci) {
-    if ((rc = finish(slot)) != NS_OK) break;
-    if ((rc = enqueue(plan.chunks[ci], slot)) != NS_OK) {
-      // copies of this chunk may be in flight: the caller's memory and the
-      // staging must be idle before returning
-      (void)hipStreamSynchronize(ctx->stream[slot]);
-      (void)hipGetLastError();
-      break;
-    }
-    pend[slot] = (int64_t)ci;
-    slot = (slot + 1) % nslots;
-  }
-  for (uint32_t k = 0; k < nslots; ++k) {
-    const int r = finish((slot + k) % nslots);
-    if (rc == NS_OK) rc = r;
-  }
-  return rc;
+  auto finish = [&](Chunk c, uint32_t sl) -> int {
+    HIP_TRY(hipEventSynchronize(ctx->done[sl]));
+    patch_tx_fields(plan, *c, ctx->h_out[sl].p, h_arena, h_out);
+    return NS_OK;
+  };
+  return nsh::run_slots<Chunk>(ctx->nslots, next, enqueue, finish, quiesce_slot(ctx));
 }
 
-// ns_csum_rx_ring_host's pipeline: the ring in chunks of whole slots (as
-// many as the staging budget holds), nslots in flight on the host pipeline's
-// streams.  Per chunk: the slots and their lengths go to the device, rx_ring
-// parses and verifies them there and writes verdicts and sums straight to
-// mapped pinned memory; when the chunk is done they are copied to the
-// caller's arrays while later chunks are in flight.  No host planning.
+// The rx_ring kernel's geometry for `n` slots of ring `r` at device address
+// `ring` (ns_csum_rx_ring and _host; ns_csum_rx_bufs adds its offsets).
+nsk::RxGeo rx_geo(const ns_csum_ctx* ctx, const ns_rx_ring& r, uint64_t ring, uint32_t n, const uint32_t* len,
+                  uint16_t* sums, uint8_t* verdict) {
+  nsk::RxGeo geo{};
+  geo.ring = ring;
+  geo.stride = r.stride;
+  geo.len = len;
+  geo.sums = sums;
+  geo.verdict = verdict;
+  geo.err = ctx->d_err;
+  geo.n = n;
+  geo.frame_at = r.frame_at;
+  geo.link = r.link_hdr;
+  geo.view0 = r.first_view ? r.first_view - r.link_hdr : 0u;
+  return geo;
+}
+
+// The same for the tx_ring kernel (ns_csum_tx_ring and _host).
+nsk::TxRingGeo tx_ring_geo(const ns_csum_ctx* ctx, const ns_tx_ring& r, uint64_t ring, uint32_t n,
+                           const uint32_t* len, uint16_t* sums, uint8_t* status, uint8_t* at) {
+  nsk::TxRingGeo geo{};
+  geo.ring = ring;
+  geo.stride = r.stride;
+  geo.len = len;
+  geo.sums = sums;
+  geo.status = status;
+  geo.at = at;
+  geo.err = ctx->d_err;
+  geo.n = n;
+  geo.frame_at = r.frame_at;
+  geo.link = r.link_hdr;
+  geo.flags = r.flags;
+  return geo;
+}
+
 // A small ring (its slots and lengths within kHostSmallBytes and the staging
-// budget) takes no DMA either: written through the BAR into a gather stage,
-// one launch, one wait.
+// budget) takes no DMA: written through the BAR into a gather stage, one
+// launch, one wait.
 int run_rx_small(ns_csum_ctx* ctx, const uint8_t* h_arena, const ns_rx_ring& r, const uint32_t* h_len,
                  uint16_t* h_sums, uint8_t* h_verdict) {
   const uint64_t bytes = (uint64_t)r.n * r.stride, len_at = (bytes + 255) & ~255ull;
@@ -1053,17 +1056,9 @@ int run_rx_small(ns_csum_ctx* ctx, const uint8_t* h_arena, const ns_rx_ring& r, 
   std::memcpy(st->p, h_arena + r.ring_off, bytes);
   std::memcpy(st->p + len_at, h_len, 4 * (size_t)r.n);
   __builtin_ia32_sfence();  // drain the write-combined BAR stores before the launch
-  nsk::RxGeo geo{};
-  geo.ring = (uint64_t)(uintptr_t)st->dev;
-  geo.stride = r.stride;
-  geo.len = reinterpret_cast<const uint32_t*>(st->dev + len_at);
-  geo.sums = reinterpret_cast<uint16_t*>(ctx->p_res.dev);
-  geo.verdict = ctx->p_res.dev + 4 * (size_t)r.n;
-  geo.err = ctx->d_err;
-  geo.n = r.n;
-  geo.frame_at = r.frame_at;
-  geo.link = r.link_hdr;
-  geo.view0 = r.first_view ? r.first_view - r.link_hdr : 0u;
+  const nsk::RxGeo geo = rx_geo(ctx, r, (uint64_t)(uintptr_t)st->dev, r.n,
+                                reinterpret_cast<const uint32_t*>(st->dev + len_at),
+                                reinterpret_cast<uint16_t*>(ctx->p_res.dev), ctx->p_res.dev + 4 * (size_t)r.n);
   hipStream_t s = ctx->stream[0];
   const hipError_t e = nsk::launch_rx_ring(geo, s);
   rc = e == hipSuccess ? wait_small(ctx, s) : report_hip(e, "run_rx_small", __FILE__, __LINE__);
@@ -1074,149 +1069,85 @@ int run_rx_small(ns_csum_ctx* ctx, const uint8_t* h_arena, const ns_rx_ring& r, 
   return NS_OK;
 }
 
+// The ring pipelines' chunks are whole slots, as many as the staging budget
+// holds (nsh::RingChunks).  The first half of their `enqueue`: slot sl's
+// buffers sized for chunk c (`verd` bytes of mapped report beside the sums),
+// then its ring slots (`ring` = the caller's slot 0) and lengths on their way
+// to the device.
+int upload_ring_chunk(ns_csum_ctx* ctx, const uint8_t* ring, uint64_t stride, const uint32_t* h_len,
+                      const nsh::RingChunk& c, uint32_t sl, uint64_t verd) {
+  int rc;
+  const uint64_t bytes = (uint64_t)c.count * stride;
+  if ((rc = ctx->d_arena[sl].ensure(bytes)) != NS_OK) return rc;
+  if ((rc = ctx->d_len[sl].ensure(c.count)) != NS_OK) return rc;
+  if ((rc = ctx->h_out[sl].ensure(2 * (size_t)c.count)) != NS_OK) return rc;
+  if ((rc = ctx->h_verd[sl].ensure(verd)) != NS_OK) return rc;
+  hipStream_t s = ctx->stream[sl];
+  HIP_TRY(hipMemcpyAsync(ctx->d_arena[sl].p, ring + (uint64_t)c.first * stride, bytes, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(ctx->d_len[sl].p, h_len + c.first, 4 * (size_t)c.count, hipMemcpyHostToDevice, s));
+  return NS_OK;
+}
+
+// ns_csum_rx_ring_host's pipeline.  Per chunk: the slots and their lengths go
+// to the device, rx_ring parses and verifies them there and writes verdicts
+// and sums straight to mapped pinned memory; when the chunk is done they are
+// copied to the caller's arrays while later chunks are in flight.  No host
+// planning.
 int run_rx_host(ns_csum_ctx* ctx, const uint8_t* h_arena, const ns_rx_ring& r, const uint32_t* h_len,
                 uint16_t* h_sums, uint8_t* h_verdict) {
   const uint64_t small = (((uint64_t)r.n * r.stride + 255) & ~255ull) + 4ull * r.n;
   if (zero_copy_enabled() && small <= std::min<uint64_t>(kHostSmallBytes, ctx->staging))
     return run_rx_small(ctx, h_arena, r, h_len, h_sums, h_verdict);
-  const uint32_t nslots = ctx->nslots;
-  const uint32_t per = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(1, ctx->staging / r.stride), 1u << 24);
-  struct Pending {
-    bool live = false;
-    uint32_t first = 0, count = 0;
-  } pend[kMaxHostSlots];
-  auto finish = [&](uint32_t sl) -> int {
-    if (!pend[sl].live) return NS_OK;
-    pend[sl].live = false;
-    HIP_TRY(hipEventSynchronize(ctx->done[sl]));
-    if (h_sums) std::memcpy(h_sums + 2 * (uint64_t)pend[sl].first, ctx->h_out[sl].p, 4 * (size_t)pend[sl].count);
-    if (h_verdict) std::memcpy(h_verdict + pend[sl].first, ctx->h_verd[sl].p, pend[sl].count);
-    return NS_OK;
-  };
-  auto enqueue = [&](uint32_t first, uint32_t cnt, uint32_t sl) -> int {
-    int rc;
-    const uint64_t bytes = (uint64_t)cnt * r.stride;
-    if ((rc = ctx->d_arena[sl].ensure(bytes)) != NS_OK) return rc;
-    if ((rc = ctx->d_len[sl].ensure(cnt)) != NS_OK) return rc;
-    if ((rc = ctx->h_out[sl].ensure(2 * (size_t)cnt)) != NS_OK) return rc;
-    if ((rc = ctx->h_verd[sl].ensure(cnt)) != NS_OK) return rc;
+  auto enqueue = [&](const nsh::RingChunk& c, uint32_t sl) -> int {
+    const int rc = upload_ring_chunk(ctx, h_arena + r.ring_off, r.stride, h_len, c, sl, c.count);
+    if (rc != NS_OK) return rc;
     hipStream_t s = ctx->stream[sl];
-    HIP_TRY(hipMemcpyAsync(ctx->d_arena[sl].p, h_arena + r.ring_off + (uint64_t)first * r.stride, bytes,
-                           hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(ctx->d_len[sl].p, h_len + first, 4 * (size_t)cnt, hipMemcpyHostToDevice, s));
-    nsk::RxGeo geo{};
-    geo.ring = (uint64_t)(uintptr_t)ctx->d_arena[sl].p;
-    geo.stride = r.stride;
-    geo.len = ctx->d_len[sl].p;
-    geo.sums = ctx->h_out[sl].dev;
-    geo.verdict = ctx->h_verd[sl].dev;
-    geo.err = ctx->d_err;
-    geo.n = cnt;
-    geo.frame_at = r.frame_at;
-    geo.link = r.link_hdr;
-    geo.view0 = r.first_view ? r.first_view - r.link_hdr : 0u;
-    HIP_TRY(nsk::launch_rx_ring(geo, s));
+    HIP_TRY(nsk::launch_rx_ring(rx_geo(ctx, r, (uint64_t)(uintptr_t)ctx->d_arena[sl].p, c.count, ctx->d_len[sl].p,
+                                       ctx->h_out[sl].dev, ctx->h_verd[sl].dev),
+                                s));
     HIP_TRY(hipEventRecord(ctx->done[sl], s));
     return NS_OK;
   };
-  int rc = NS_OK;
-  uint32_t slot = 0;
-  for (uint64_t f = 0; f < r.n; f += per) {  // 64-bit: first + per may pass 2^32
-    const uint32_t first = (uint32_t)f;
-    const uint32_t cnt = (uint32_t)std::min<uint64_t>(per, r.n - f);
-    if ((rc = finish(slot)) != NS_OK) break;
-    if ((rc = enqueue(first, cnt, slot)) != NS_OK) {
-      (void)hipStreamSynchronize(ctx->stream[slot]);
-      (void)hipGetLastError();
-      break;
-    }
-    pend[slot].live = true;
-    pend[slot].first = first;
-    pend[slot].count = cnt;
-    slot = (slot + 1) % nslots;
-  }
-  for (uint32_t k = 0; k < nslots; ++k) {
-    const int e = finish((slot + k) % nslots);
-    if (rc == NS_OK) rc = e;
-  }
-  return rc;
+  auto finish = [&](const nsh::RingChunk& c, uint32_t sl) -> int {
+    HIP_TRY(hipEventSynchronize(ctx->done[sl]));
+    if (h_sums) std::memcpy(h_sums + 2 * (uint64_t)c.first, ctx->h_out[sl].p, 4 * (size_t)c.count);
+    if (h_verdict) std::memcpy(h_verdict + c.first, ctx->h_verd[sl].p, c.count);
+    return NS_OK;
+  };
+  return nsh::run_slots<nsh::RingChunk>(ctx->nslots, nsh::RingChunks(r.n, ctx->staging, r.stride), enqueue, finish,
+                                        quiesce_slot(ctx));
 }
 
-// ns_csum_tx_ring_host's pipeline, run_rx_host's shape: the ring in chunks of
-// whole slots, nslots in flight on the host pipeline's streams.  Per chunk:
-// the slots and their lengths go to the device, tx_ring parses them there,
-// fills the staged copy and writes status, sums and each transport field's
-// place straight to mapped pinned memory; when the chunk is done the fields
-// are written into the caller's ring from that report (nsh::tx_ring_patch)
-// while later chunks are in flight.  No host parsing, no copy back.
+// ns_csum_tx_ring_host's pipeline.  Per chunk: the slots and their lengths go
+// to the device, tx_ring parses them there, fills the staged copy and writes
+// status, sums and each transport field's place straight to mapped pinned
+// memory (status in the mapped report's first count bytes, the places after);
+// when the chunk is done the fields are written into the caller's ring from
+// that report (nsh::tx_ring_patch) while later chunks are in flight.  No host
+// parsing, no copy back.
 int run_tx_ring_host(ns_csum_ctx* ctx, uint8_t* h_arena, const ns_tx_ring& r, const uint32_t* h_len,
                      uint16_t* h_sums, uint8_t* h_status) {
-  const uint32_t nslots = ctx->nslots;
-  const uint32_t per = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(1, ctx->staging / r.stride), 1u << 24);
-  struct Pending {
-    bool live = false;
-    uint32_t first = 0, count = 0;
-  } pend[kMaxHostSlots];
-  auto finish = [&](uint32_t sl) -> int {
-    if (!pend[sl].live) return NS_OK;
-    pend[sl].live = false;
-    HIP_TRY(hipEventSynchronize(ctx->done[sl]));
-    const uint32_t first = pend[sl].first, cnt = pend[sl].count;
-    // status in the mapped buffer's first cnt bytes, the fields' places after
-    nsh::tx_ring_patch(h_arena + r.ring_off, r.stride, (uint32_t)r.frame_at + r.link_hdr, h_len, first, cnt,
-                       ctx->h_out[sl].p, ctx->h_verd[sl].p + cnt);
-    if (h_sums) std::memcpy(h_sums + 2 * (uint64_t)first, ctx->h_out[sl].p, 4 * (size_t)cnt);
-    if (h_status) std::memcpy(h_status + first, ctx->h_verd[sl].p, cnt);
-    return NS_OK;
-  };
-  auto enqueue = [&](uint32_t first, uint32_t cnt, uint32_t sl) -> int {
-    int rc;
-    const uint64_t bytes = (uint64_t)cnt * r.stride;
-    if ((rc = ctx->d_arena[sl].ensure(bytes)) != NS_OK) return rc;
-    if ((rc = ctx->d_len[sl].ensure(cnt)) != NS_OK) return rc;
-    if ((rc = ctx->h_out[sl].ensure(2 * (size_t)cnt)) != NS_OK) return rc;
-    if ((rc = ctx->h_verd[sl].ensure(2 * (uint64_t)cnt)) != NS_OK) return rc;
+  auto enqueue = [&](const nsh::RingChunk& c, uint32_t sl) -> int {
+    const int rc = upload_ring_chunk(ctx, h_arena + r.ring_off, r.stride, h_len, c, sl, 2 * (uint64_t)c.count);
+    if (rc != NS_OK) return rc;
     hipStream_t s = ctx->stream[sl];
-    HIP_TRY(hipMemcpyAsync(ctx->d_arena[sl].p, h_arena + r.ring_off + (uint64_t)first * r.stride, bytes,
-                           hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(ctx->d_len[sl].p, h_len + first, 4 * (size_t)cnt, hipMemcpyHostToDevice, s));
-    nsk::TxRingGeo geo{};
-    geo.ring = (uint64_t)(uintptr_t)ctx->d_arena[sl].p;
-    geo.stride = r.stride;
-    geo.len = ctx->d_len[sl].p;
-    geo.sums = ctx->h_out[sl].dev;
-    geo.status = ctx->h_verd[sl].dev;
-    geo.at = ctx->h_verd[sl].dev + cnt;
-    geo.err = ctx->d_err;
-    geo.n = cnt;
-    geo.frame_at = r.frame_at;
-    geo.link = r.link_hdr;
-    geo.flags = r.flags;
-    HIP_TRY(nsk::launch_tx_ring(geo, s));
+    HIP_TRY(nsk::launch_tx_ring(tx_ring_geo(ctx, r, (uint64_t)(uintptr_t)ctx->d_arena[sl].p, c.count,
+                                            ctx->d_len[sl].p, ctx->h_out[sl].dev, ctx->h_verd[sl].dev,
+                                            ctx->h_verd[sl].dev + c.count),
+                                s));
     HIP_TRY(hipEventRecord(ctx->done[sl], s));
     return NS_OK;
   };
-  int rc = NS_OK;
-  uint32_t slot = 0;
-  for (uint64_t f = 0; f < r.n; f += per) {  // 64-bit: first + per may pass 2^32
-    const uint32_t first = (uint32_t)f;
-    const uint32_t cnt = (uint32_t)std::min<uint64_t>(per, r.n - f);
-    if ((rc = finish(slot)) != NS_OK) break;
-    if ((rc = enqueue(first, cnt, slot)) != NS_OK) {
-      (void)hipStreamSynchronize(ctx->stream[slot]);
-      (void)hipGetLastError();
-      break;
-    }
-    pend[slot].live = true;
-    pend[slot].first = first;
-    pend[slot].count = cnt;
-    slot = (slot + 1) % nslots;
-  }
-  for (uint32_t k = 0; k < nslots; ++k) {
-    const int e = finish((slot + k) % nslots);
-    if (rc == NS_OK) rc = e;
-  }
-  return rc;
+  auto finish = [&](const nsh::RingChunk& c, uint32_t sl) -> int {
+    HIP_TRY(hipEventSynchronize(ctx->done[sl]));
+    nsh::tx_ring_patch(h_arena + r.ring_off, r.stride, (uint32_t)r.frame_at + r.link_hdr, h_len, c.first, c.count,
+                       ctx->h_out[sl].p, ctx->h_verd[sl].p + c.count);
+    if (h_sums) std::memcpy(h_sums + 2 * (uint64_t)c.first, ctx->h_out[sl].p, 4 * (size_t)c.count);
+    if (h_status) std::memcpy(h_status + c.first, ctx->h_verd[sl].p, c.count);
+    return NS_OK;
+  };
+  return nsh::run_slots<nsh::RingChunk>(ctx->nslots, nsh::RingChunks(r.n, ctx->staging, r.stride), enqueue, finish,
+                                        quiesce_slot(ctx));
 }
 
 // Caller-acquired staging (ns_csum_stage_acquire): mapped pinned buffers a
@@ -1900,17 +1831,7 @@ int ns_csum_rx_ring(ns_csum_ctx* ctx, const uint8_t* d_arena, uint64_t arena_byt
   if (vr != NS_OK) return vr;
   if (r.n == 0) return NS_OK;
   DeviceGuard g(ctx->device);
-  nsk::RxGeo geo{};
-  geo.ring = base + r.ring_off;
-  geo.stride = r.stride;
-  geo.len = d_len;
-  geo.sums = d_sums;
-  geo.verdict = d_verdict;
-  geo.err = ctx->d_err;
-  geo.n = r.n;
-  geo.frame_at = r.frame_at;
-  geo.link = r.link_hdr;
-  geo.view0 = r.first_view ? r.first_view - r.link_hdr : 0u;
+  const nsk::RxGeo geo = rx_geo(ctx, r, base + r.ring_off, r.n, d_len, d_sums, d_verdict);
   HIP_TRY(nsk::launch_rx_ring(geo, (hipStream_t)stream));
   return NS_OK;
 }
@@ -1932,17 +1853,7 @@ int ns_csum_rx_bufs(ns_csum_ctx* ctx, const uint8_t* d_arena, uint64_t arena_byt
   if (limit > (1ull << 32) - 512) return NS_EINVAL;  // 32-bit offsets under one buffer resource
   if (r.n == 0) return NS_OK;
   DeviceGuard g(ctx->device);
-  nsk::RxGeo geo{};
-  geo.ring = base + r.ring_off;
-  geo.stride = r.stride;
-  geo.len = d_len;
-  geo.sums = d_sums;
-  geo.verdict = d_verdict;
-  geo.err = ctx->d_err;
-  geo.n = r.n;
-  geo.frame_at = r.frame_at;
-  geo.link = r.link_hdr;
-  geo.view0 = r.first_view ? r.first_view - r.link_hdr : 0u;
+  nsk::RxGeo geo = rx_geo(ctx, r, base + r.ring_off, r.n, d_len, d_sums, d_verdict);
   geo.off = d_off;
   geo.limit = limit;
   HIP_TRY(nsk::launch_rx_ring(geo, (hipStream_t)stream));
@@ -1977,17 +1888,8 @@ int ns_csum_tx_ring(ns_csum_ctx* ctx, uint8_t* d_arena, uint64_t arena_bytes, co
   if (vr != NS_OK) return vr;
   if (r.n == 0) return NS_OK;
   DeviceGuard g(ctx->device);
-  nsk::TxRingGeo geo{};
-  geo.ring = base + r.ring_off;
-  geo.stride = r.stride;
-  geo.len = d_len;
-  geo.sums = d_sums;
-  geo.status = d_status;
-  geo.err = ctx->d_err;
-  geo.n = r.n;
-  geo.frame_at = r.frame_at;
-  geo.link = r.link_hdr;
-  geo.flags = r.flags;
+  // the fields' places are reported to the host path only
+  const nsk::TxRingGeo geo = tx_ring_geo(ctx, r, base + r.ring_off, r.n, d_len, d_sums, d_status, nullptr);
   HIP_TRY(nsk::launch_tx_ring(geo, (hipStream_t)stream));
   return NS_OK;
 }

@@ -6,6 +6,7 @@
 //   - ChainBuilder: chains of restart/continue pieces -> ns_pkt_desc runs;
 //   - PacketBytes / plan_packet: tcpip.PacketBuffer checksum steps;
 //   - cut_chunk: the host pipeline's chunking of a descriptor table;
+//   - run_slots: the host pipelines' rotation of chunks over the slots;
 //   - shard_plan: byte-balanced contiguous shards;
 //   - ScratchRegistry: per-stream scratch bookkeeping (LRU, pins, release);
 //   - FlatCombiner: flat combining of concurrent small synchronous calls.
@@ -586,6 +587,95 @@ inline int cut_chunk(const ns_pkt_desc* d, uint32_t n, uint32_t k, uint64_t aren
   *hi_out = cut_hi;
   return NS_OK;
 }
+
+// ---- the host pipelines' slot rotation --------------------------------------
+// ns_csum_batch_host, ns_csum_tcp_tx_host, ns_csum_rx_ring_host and
+// ns_csum_tx_ring_host send host memory to the device in chunks, up to
+// `nslots` (1..kMaxHostSlots) of them in flight, each on its slot's stream
+// and staging.  run_slots is that rotation and nothing else (no HIP here):
+//   next(Chunk*)          NS_OK with the next chunk filled in, kSlotsDone when
+//                         there are no more, or an error;
+//   enqueue(chunk, slot)  queues the chunk's copies, launch and event on the
+//                         slot's stream;
+//   finish(chunk, slot)   waits for the slot's event and delivers the chunk's
+//                         results to the caller;
+//   quiesce(slot)         makes the slot's stream idle after a failed enqueue
+//                         (never fails).
+// Chunk is the caller's own trivially copyable description of one chunk.
+// The contract:
+//   - chunk i uses slot i % nslots;
+//   - per chunk: next, then finish of the slot's previous chunk if it is
+//     live, then enqueue — next comes first so the CPU prepares the chunk
+//     (cut_chunk's scan of the table) while the device still works;
+//   - a chunk is live from its enqueue returning NS_OK until its finish;
+//   - the first error from next, finish or enqueue ends the queueing: nothing
+//     more is fetched or enqueued.  If it came from enqueue(c, slot),
+//     quiesce(slot) runs once, before anything else (copies of the failed
+//     chunk may be in flight from the caller's memory into the staging);
+//   - at the end, with or without an error, every live chunk is finished,
+//     oldest first, even after a failing finish: the caller's memory and the
+//     staging are idle on return, and chunks that completed deliver their
+//     results;
+//   - the first error that occurred is returned, NS_OK if none.
+constexpr uint32_t kMaxHostSlots = 4;
+constexpr int kSlotsDone = 1;  // next(): no more chunks (statuses are <= 0)
+
+template <class Chunk, class Next, class Enqueue, class Finish, class Quiesce>
+int run_slots(uint32_t nslots, Next&& next, Enqueue&& enqueue, Finish&& finish, Quiesce&& quiesce) {
+  if (nslots == 0 || nslots > kMaxHostSlots) return NS_EINVAL;
+  struct {
+    bool live = false;
+    Chunk c;
+  } pend[kMaxHostSlots];
+  int rc = NS_OK;
+  auto retire = [&](uint32_t s) {
+    if (!pend[s].live) return;
+    pend[s].live = false;
+    const int e = finish(pend[s].c, s);
+    if (rc == NS_OK) rc = e;
+  };
+  uint32_t slot = 0;  // the next chunk's; the live chunks from it on are oldest first
+  while (rc == NS_OK) {
+    Chunk c{};
+    const int e = next(&c);
+    if (e == kSlotsDone) break;
+    if (e != NS_OK) {
+      rc = e;
+      break;
+    }
+    retire(slot);
+    if (rc != NS_OK) break;
+    if ((rc = enqueue(c, slot)) != NS_OK) {
+      quiesce(slot);
+      break;
+    }
+    pend[slot].live = true;
+    pend[slot].c = c;
+    slot = (slot + 1) % nslots;
+  }
+  for (uint32_t k = 0; k < nslots; ++k) retire((slot + k) % nslots);
+  return rc;
+}
+
+// The chunks of a ring of `n` slots of `stride` bytes (ns_csum_rx_ring_host,
+// ns_csum_tx_ring_host): whole slots, as many as `staging` bytes hold (one at
+// least, 2^24 at most), as a run_slots `next`.
+struct RingChunk {
+  uint32_t first, count;  // slots [first, first + count)
+};
+struct RingChunks {
+  uint64_t at = 0;  // 64-bit: at + per may pass 2^32
+  uint32_t n, per;
+  RingChunks(uint32_t slots, uint64_t staging, uint64_t stride)
+      : n(slots), per((uint32_t)std::min<uint64_t>(std::max<uint64_t>(1, staging / stride), 1u << 24)) {}
+  int operator()(RingChunk* c) {
+    if (at >= n) return kSlotsDone;
+    c->first = (uint32_t)at;
+    c->count = (uint32_t)std::min<uint64_t>(per, n - at);
+    at += per;
+    return NS_OK;
+  }
+};
 
 // ---- sharding (ns_csum_shard_plan) -------------------------------------------
 // Splits n descriptors into `parts` contiguous ranges with near-equal payload

@@ -13,6 +13,9 @@
 //                 packets verify;
 //   cut_chunk     chunks tile the table, never end inside a chained run,
 //                 spans within budget, NS_ERANGE on a bad descriptor;
+//   run_slots     every slot count and chunk count, a failure injected at
+//                 every callback: slot assignment, the order of the steps,
+//                 what runs after an error and which error is returned;
 //   shard_plan    contiguous, ordered, whole runs, byte-balanced;
 //   tx_plan, tx_multi_plan, rx_plan  geometry checks: whatever they accept
 //                 stays inside the arena and apart where the kernels need it;
@@ -379,6 +382,134 @@ static void TestCutChunk(Rng& rng, int rounds) {
         kk = cut;
       CHECK(rc == NS_ERANGE, "bad descriptor -> NS_ERANGE (%d)", rc);
     }
+  }
+}
+
+// nsh::run_slots (the host pipelines' rotation) over fake callbacks that
+// record a trace.  Chunk i is the int i; `fail_next`, `fail_enqueue` and
+// `fail_finish` name the chunk whose callback fails (-1: none), each with a
+// status of its own.  Every trace is replayed against the contract in
+// host_logic.h; `want` is the status the call must return.
+struct SlotEvent {
+  char kind;  // 'n'ext, 'e'nqueue, 'f'inish, 'q'uiesce
+  int chunk;  // 'q': -1
+  uint32_t slot;
+  int rc;
+};
+static void RunSlotsCase(uint32_t nslots, int nchunks, int fail_next, int fail_enqueue, int fail_finish, int want) {
+  std::vector<SlotEvent> tr;
+  int k = 0;
+  auto next = [&](int* c) -> int {
+    const int rc = k == fail_next ? NS_ERANGE : k == nchunks ? nsh::kSlotsDone : NS_OK;
+    tr.push_back({'n', k, 0, rc});
+    if (rc == NS_OK) *c = k++;
+    return rc;
+  };
+  auto enqueue = [&](const int& c, uint32_t s) -> int {
+    tr.push_back({'e', c, s, c == fail_enqueue ? NS_ENOMEM : NS_OK});
+    return tr.back().rc;
+  };
+  auto finish = [&](const int& c, uint32_t s) -> int {
+    tr.push_back({'f', c, s, c == fail_finish ? NS_EHIP : NS_OK});
+    return tr.back().rc;
+  };
+  auto quiesce = [&](uint32_t s) { tr.push_back({'q', -1, s, NS_OK}); };
+  const int got = nsh::run_slots<int>(nslots, next, enqueue, finish, quiesce);
+
+  int first_err = NS_OK, fetched = 0, enqueued = 0, quiesced = 0, failed_enqueue = -1;
+  bool done = false;
+  std::vector<int> live;                           // enqueued and not finished, oldest first
+  std::vector<int> in_slot(nsh::kMaxHostSlots, -1);  // the live chunk of each slot
+  for (size_t i = 0; i < tr.size(); ++i) {
+    const SlotEvent& e = tr[i];
+    const SlotEvent* prev = i ? &tr[i - 1] : nullptr;
+    if (e.kind == 'n') {
+      CHECK(first_err == NS_OK && !done, "next(%d) after the end", e.chunk);
+      CHECK(e.chunk == fetched, "next %d, want %d", e.chunk, fetched);
+      if (e.rc == NS_OK) ++fetched;
+      if (e.rc == nsh::kSlotsDone) done = true;
+    } else if (e.kind == 'e') {
+      CHECK(first_err == NS_OK && !done, "enqueue(%d) after the end", e.chunk);
+      CHECK(e.chunk == enqueued && e.chunk == fetched - 1, "enqueue %d: %d enqueued, %d fetched", e.chunk, enqueued,
+            fetched);
+      CHECK(e.slot == (uint32_t)e.chunk % nslots, "chunk %d on slot %u", e.chunk, e.slot);
+      CHECK(in_slot[e.slot] < 0, "slot %u holds chunk %d", e.slot, in_slot[e.slot]);
+      CHECK(live.size() < nslots, "%zu live chunks", live.size());
+      // the chunk's own steps: next, finish of the slot's previous chunk, enqueue
+      if (e.chunk >= (int)nslots)
+        CHECK(prev && prev->kind == 'f' && prev->chunk == e.chunk - (int)nslots && i >= 2 && tr[i - 2].kind == 'n' &&
+                  tr[i - 2].chunk == e.chunk,
+              "steps before enqueue(%d)", e.chunk);
+      else
+        CHECK(prev && prev->kind == 'n' && prev->chunk == e.chunk, "steps before enqueue(%d)", e.chunk);
+      ++enqueued;
+      if (e.rc == NS_OK) {
+        live.push_back(e.chunk);
+        in_slot[e.slot] = e.chunk;
+      } else {
+        failed_enqueue = e.chunk;
+        CHECK(i + 1 < tr.size() && tr[i + 1].kind == 'q' && tr[i + 1].slot == e.slot, "no quiesce behind enqueue(%d)",
+              e.chunk);
+      }
+    } else if (e.kind == 'f') {
+      CHECK(!live.empty() && live.front() == e.chunk, "finish(%d) out of order", e.chunk);
+      CHECK(e.chunk != failed_enqueue, "finish of the chunk whose enqueue failed");
+      CHECK(in_slot[e.slot] == e.chunk, "finish(%d) on slot %u", e.chunk, e.slot);
+      if (!live.empty() && live.front() == e.chunk) live.erase(live.begin());
+      in_slot[e.slot] = -1;
+    } else {
+      CHECK(prev && prev->kind == 'e' && prev->rc != NS_OK && prev->slot == e.slot, "a stray quiesce(%u)", e.slot);
+      ++quiesced;
+    }
+    if (first_err == NS_OK && e.rc < 0) first_err = e.rc;
+  }
+  CHECK(live.empty(), "%zu chunks never finished", live.size());
+  CHECK(quiesced == (failed_enqueue >= 0 ? 1 : 0), "%d quiesce calls", quiesced);
+  CHECK(got == first_err && got == want, "returned %d, first error %d, want %d (%u slots, %d chunks, fail %d/%d/%d)",
+        got, first_err, want, nslots, nchunks, fail_next, fail_enqueue, fail_finish);
+  if (want == NS_OK) CHECK(done && enqueued == nchunks, "%d of %d chunks enqueued", enqueued, nchunks);
+}
+
+static void TestRunSlots(Rng& rng) {
+  int cases = 0;
+  for (uint32_t nslots = 1; nslots <= nsh::kMaxHostSlots; ++nslots) {
+    for (int n = 0; n <= 3 * (int)nslots + 2; ++n) {
+      RunSlotsCase(nslots, n, -1, -1, -1, NS_OK);
+      for (int j = 0; j <= n; ++j) RunSlotsCase(nslots, n, j, -1, -1, NS_ERANGE);  // j == n: in place of the end
+      for (int j = 0; j < n; ++j) {
+        RunSlotsCase(nslots, n, -1, j, -1, NS_ENOMEM);
+        RunSlotsCase(nslots, n, -1, -1, j, NS_EHIP);
+        // enqueue(j) fails; finish(i) fails too: in the drain if chunk i is
+        // live then (the enqueue's status wins), before enqueue(j) otherwise
+        for (int i = 0; i < j; ++i, ++cases)
+          RunSlotsCase(nslots, n, -1, j, i, i > j - (int)nslots ? NS_ENOMEM : NS_EHIP);
+        // next(j) fails, then finish(i) in the drain
+        for (int i = std::max(0, j - (int)nslots); i < j; ++i) RunSlotsCase(nslots, n, j, -1, i, NS_ERANGE);
+      }
+    }
+  }
+  CHECK(cases > 100, "%d double-failure cases", cases);
+  int dummy = 0;
+  auto none = [&](int*) { return (int)nsh::kSlotsDone; };
+  auto ok = [&](const int&, uint32_t) { return ++dummy, (int)NS_OK; };
+  CHECK(nsh::run_slots<int>(0, none, ok, ok, [](uint32_t) {}) == NS_EINVAL, "no slots");
+  CHECK(nsh::run_slots<int>(nsh::kMaxHostSlots + 1, none, ok, ok, [](uint32_t) {}) == NS_EINVAL, "too many slots");
+  // nsh::RingChunks: whole slots within the staging budget (one at least,
+  // 2^24 at most) that tile the ring, up to a ring of 2^32 - 1 slots
+  for (int round = 0; round < 300; ++round) {
+    const uint64_t stride = 16 * (1 + rng() % 200);
+    const uint64_t staging = round == 0 ? 1ull << 40 : round % 3 == 0 ? rng() % (4 * stride) : rng() % (1ull << 28);
+    const uint32_t n = round == 0 ? 0xFFFFFFFFu : round == 1 ? 0 : (uint32_t)(rng() % 100000);
+    const uint64_t per = std::min<uint64_t>(std::max<uint64_t>(1, staging / stride), 1u << 24);
+    nsh::RingChunks next(n, staging, stride);
+    nsh::RingChunk c{};
+    uint64_t at = 0;
+    int rc;
+    while ((rc = next(&c)) == NS_OK) {
+      if (c.first != at || c.count == 0 || c.count > per || (c.count < per && at + c.count != n)) break;
+      at += c.count;
+    }
+    CHECK(rc == nsh::kSlotsDone && at == n, "ring of %u slots: stopped at %llu (%d)", n, (unsigned long long)at, rc);
   }
 }
 
@@ -893,6 +1024,7 @@ int main(int argc, char** argv) {
   TestTxHostPlan(rng, r);
   TestTxShardCalls(rng, r);
   TestRxPlan(rng, r);
+  TestRunSlots(rng);
   TestCombiner(16, quick ? 200 : 2000);
   TestScratchRegistry(8, 1000, quick ? 2000 : 20000);
   std::printf("%d checks, %d failed\n", g_run.load(), g_fail.load());
